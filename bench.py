@@ -43,7 +43,6 @@ except AttributeError:
     AFFINITY_CPUS = os.cpu_count() or 1
 # the cpu_baseline leg times OpenMP code (oracle/_ref): pin its threads to cores, one per core, before any OpenMP runtime
 # is loaded - unpinned threads of a dynamic schedule migrate and the number is not reproducible
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # streams of the MAC length classes (hhv_create): before HIP initialises
 os.environ.setdefault("OMP_PROC_BIND", "close")
 os.environ.setdefault("OMP_PLACES", "cores")
 
@@ -108,9 +107,16 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="one rank: still go through torch.distributed (nccl = RCCL) for the hit-list exchange")
     ap.add_argument("--dump-topk", default=None, help="rank 0 writes the merged top-K of the last step (global id, score bits) as .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned - the merged hit list, one DIR/hits_<field>.npy per hhv_hit "
+                         "field (float32 scores, float64 integers) - so that two builds can be compared output for output")
     if len(sys.argv) == 1 and os.environ.get("HHV_BENCH_ARGV"):   # a rank started by respawn() below
-        return ap.parse_args(json.loads(os.environ["HHV_BENCH_ARGV"]))
-    return ap.parse_args()
+        args = ap.parse_args(json.loads(os.environ["HHV_BENCH_ARGV"]))
+    else:
+        args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port():
@@ -137,7 +143,27 @@ def respawn(args):
     env["HHV_BENCH_ARGV"] = json.dumps(sys.argv[1:])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)]
-    os.execvpe(cmd[0], cmd, env)
+    # a fresh child process, not an exec of this one: this process has already brought up HIP (capi.device_count)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd, env=env))
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the merged hit list of the last timed step (valid records only, in list order), one array per hhv_hit
+    field.  Lists too large for DUMP_MAX_BYTES are cut to a fixed, seeded sample of records (list order kept)."""
+    from pyhhv import capi
+    hits = np.ascontiguousarray(records, dtype=np.int32).view(capi.HIT_DTYPE).reshape(-1)
+    cols = {f: (np.float32 if hits.dtype[f] == np.float32 else np.float64) for f in hits.dtype.names}
+    row_bytes = sum(np.dtype(t).itemsize for t in cols.values())
+    if hits.shape[0] * row_bytes > DUMP_MAX_BYTES:
+        keep = np.random.default_rng(0x0D0).choice(hits.shape[0], DUMP_MAX_BYTES // row_bytes, replace=False)
+        hits = hits[np.sort(keep)]
+    os.makedirs(out_dir, exist_ok=True)
+    for f, t in cols.items():
+        np.save(os.path.join(out_dir, "hits_%s.npy" % f), hits[f].astype(t))
 
 
 def global_plan(args, capi, synth, n_per, n_shards):
@@ -334,6 +360,8 @@ def main():
         total_cells = float(cells_per_rank)
     if args.dump_topk and rank == 0:
         np.save(args.dump_topk, merged.cpu().numpy()[:, [shard.COL_INDEX, 0, 6, 7]])   # global id, score bits, i2, j2
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, merged.cpu().numpy())
 
     value = total_cells * args.steps / dt
     k_ms = float(np.mean(kernel_ms))

@@ -12,12 +12,14 @@
 // generator of bench.py in C++), a template's columns depend on its global id alone.
 //
 // Launch:  sharded_search_rccl --world N [--templates n] [--lq L] [--lt L] [--topk K] [--backtrace] [--zipf] [--steps S] [--check] [--json]
-//   the launcher forks N ranks of itself; ALL GPUs stay visible to every rank, rank r uses device r (RCCL then sees its peers
+//   the launcher spawns N ranks of itself; ALL GPUs stay visible to every rank, rank r uses device r (RCCL then sees its peers
 //   and takes the xGMI peer-to-peer transport; NCCL_DEBUG=INFO shows which), rank 0 creates the id and hands it to the others
 //   through a file; no MPI needed.
 //   --check: rank 0 also aligns the WHOLE database on its own GPU and compares the merged list with that search's top K.
 //   --json:  rank 0 prints one JSON line (per-rank DP kernel / local / all-gather / merge times, cells/s) for tools/scale8.sh
 // Build:   make example_rccl     (hipcc, -lhhv_rccl_runner -lhhviterbi_hip -lrccl)
+#include <signal.h>
+#include <spawn.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -233,7 +235,7 @@ int main(int argc, char** argv) {
   if (o.world < 1 || o.n < o.world || o.topk < 1 || o.steps < 1) return 2;
   if (o.rank >= 0) return run_rank(o);
 
-  // ---- launcher: fork one process per rank; every rank sees ALL GPUs and takes device `rank` (RCCL needs to see its peers for
+  // ---- launcher: one process per rank; every rank sees ALL GPUs and takes device `rank` (RCCL needs to see its peers for
   // the peer-to-peer transport; narrowing HIP_VISIBLE_DEVICES to one device per rank would push it to host staging)
   int32_t n_dev = 0;
   if (hhv_device_count(&n_dev) != HHV_OK || n_dev < 1) {
@@ -252,24 +254,29 @@ int main(int argc, char** argv) {
   }
   char idf[256];
   snprintf(idf, sizeof(idf), "%s/id", dir);
+  // every rank is a fresh process started with posix_spawn: this one has already brought up HIP (hhv_device_count), and a
+  // copy of it must not carry that state into a rank
   std::vector<pid_t> kids;
+  int rc = 0;
   for (int r = 0; r < o.world; ++r) {
-    const pid_t pid = fork();
-    if (pid == 0) {
-      std::vector<std::string> args(argv, argv + argc);
-      args.push_back("--rank");
-      args.push_back(std::to_string(r));
-      args.push_back("--id-file");
-      args.push_back(idf);
-      std::vector<char*> cargs;
-      for (std::string& s : args) cargs.push_back(&s[0]);
-      cargs.push_back(nullptr);
-      execv("/proc/self/exe", cargs.data());
-      _exit(127);
+    std::vector<std::string> args(argv, argv + argc);
+    args.push_back("--rank");
+    args.push_back(std::to_string(r));
+    args.push_back("--id-file");
+    args.push_back(idf);
+    std::vector<char*> cargs;
+    for (std::string& s : args) cargs.push_back(&s[0]);
+    cargs.push_back(nullptr);
+    pid_t pid = 0;
+    const int e = posix_spawn(&pid, "/proc/self/exe", nullptr, nullptr, cargs.data(), environ);
+    if (e != 0) {
+      fprintf(stderr, "posix_spawn: %s\n", strerror(e));
+      for (pid_t p : kids) kill(p, SIGTERM);   // the ranks already started would wait for their peers forever
+      rc = 127;
+      break;
     }
     kids.push_back(pid);
   }
-  int rc = 0;
   for (pid_t pid : kids) {
     int st = 0;
     waitpid(pid, &st, 0);

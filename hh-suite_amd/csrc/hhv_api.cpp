@@ -201,13 +201,8 @@ int hhv_create(hhv_ctx** out, const hhv_params* par) {
   if (!out || !par) return fail(HHV_E_ARG, "hhv_create: null argument");
   *out = nullptr;
   // The MAC realignment runs its template-length classes side by side in MAC_CHAINS streams (hhv_mac.hip launch_mac).  The HIP
-  // runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and streams that share one run one after the other:
-  // 500 hits of mixed lengths 9.2 ms with eight queues, 12.7 ms with four (tools/SESSIONS.md round 6); with eight the context's own
-  // stream, the null stream and the eight class streams still left two classes behind each other (4.9 -> 4.65 ms with sixteen).
-  // The runtime reads the variable when it initialises, so this has an effect only in a process whose first HIP call is this one
-  // (the drop-in applications); hosts that initialise HIP earlier export it themselves (pyhhv/capi.py does).  An explicit setting
-  // is respected.
-  (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);
+  // runtime maps streams onto the process's hardware queues, and streams that share one run one after the other.  How many
+  // hardware queues a process opens is the host's decision: the library does not change the process environment.
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0)

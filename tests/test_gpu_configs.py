@@ -149,6 +149,26 @@ def test_bench_two_ranks_merge_equals_one_rank(tmp_path, lengths, bt):
     assert set(owner[list(ids)].tolist()) == {0, 1}                             # hits from both shards, global ids
 
 
+def test_bench_dump_outputs_is_the_last_steps_hit_list(tmp_path):
+    """--dump-outputs DIR: the merged hit list of the last timed step, one hits_<field>.npy per hhv_hit field (float32 scores,
+    float64 integers); the same arguments give the same arrays, and they agree with --dump-topk of the same run."""
+    common = ["--templates", "3000", "--lt", "120", "--lq", "150", "--topk", "64", "--steps", "3"]
+    a = run_bench(common + ["--dump-outputs", str(tmp_path / "a"), "--dump-topk", str(tmp_path / "top.npy")])
+    run_bench(common + ["--dump-outputs", str(tmp_path / "b")])
+    assert a["steps"] == 3
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted("hits_%s.npy" % f for f in ("score", "viterbi_score", "score_ss", "index", "i1", "j1", "i2", "j2",
+                                                       "nsteps", "matched_cols"))
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.shape == (64,) and x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+    top = np.load(tmp_path / "top.npy")   # global id, score bits, i2, j2
+    assert np.array_equal(np.load(tmp_path / "a" / "hits_index.npy"), top[:, 0])
+    assert np.array_equal(np.load(tmp_path / "a" / "hits_score.npy"), top[:, 1].view(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "hits_i2.npy"), top[:, 2])
+    assert np.array_equal(np.load(tmp_path / "a" / "hits_j2.npy"), top[:, 3])
+
+
 def test_bench_one_rank_through_rccl_equals_plain_one_rank(tmp_path):
     """--force-dist: ONE rank through init_process_group("nccl") (= RCCL) + all_gather_into_tensor on device records +
     hhv_merge_hits, the streams ordered by events - the branch every multi-GPU run takes - must give the plain one-rank

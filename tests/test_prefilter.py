@@ -199,7 +199,7 @@ def test_oracle_sw_matches_reference_for_any_gap_parameters(oracle, ref, seed):
 import os
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_CS219 = "/root/reference/data/cs219.lib"
+CS219_LIB = os.path.join(GOLD, "cs219.lib")   # the reference's data/cs219.lib, byte for byte
 
 
 def _fixture():
@@ -267,11 +267,10 @@ def test_flog2_fpow2_bitwise(ref):
         assert np.float32(r.hhvr_fpow2(x)).tobytes() == np.float32(ref.lib.ref_fpow2(x)).tobytes(), x
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CS219), reason="reference data not present")
 def test_context_library_parser_matches_reference():
     from pyhhv import capi
     lib, _, _, _ = _fixture()
-    assert np.array_equal(capi.read_context_library(REF_CS219), lib)
+    assert np.array_equal(capi.read_context_library(CS219_LIB), lib)
 
 
 def test_query_profile_matches_golden():

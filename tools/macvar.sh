@@ -4,7 +4,6 @@ run() { echo -n "== $* : "; env "$@" timeout 300 python tools/bench_mac.py $SHAP
 for SHAPE in "500 300 300" "500 300 0" "500 700 0"; do
   echo "#### $SHAPE"
   run A=1
-  run GPU_MAX_HW_QUEUES=16
 done
 for SHAPE in "2000 300 300" "2000 300 0" "1000 300 300"; do
   echo "#### $SHAPE"
